@@ -13,8 +13,9 @@ set FIXED and sharded over the N ranks (strong scaling, as the north star words 
 weak-scaling companion (P = round(128 sqrt(N)): per-GPU work fixed) is `value_weak`.  Other workloads (--workload): c2 32 x 150,
 c4 512 x 300, c5 64 x 1200, each FIXED and sharded.
 
-Besides `value` (device-resident rate, SURVEY.md 8(d) and the driver's contract; the timed region of K steps is REPEATED
-`--repeats` times and `ms_per_step` / `value` are the MEDIAN run's, min / median / max in `repeats`) the line carries
+Besides `value` (device-resident rate, SURVEY.md 8(d) and the driver's contract; the timed region is EXACTLY K steps, and
+`ms_per_step` is its time over K.  `--repeats R` repeats that region R times: `ms_per_step` / `value` are then the MEDIAN run's,
+min / median / max in `repeats`) the line carries
   value_incl_transfers : the same pair set INCLUDING the upload of the structures and the download of every result, one batch with
                          a wait behind it -- the metric as SURVEY.md 8(d) words it; ..._pipelined: a two-stream pipeline of them;
   c3_sharded, c4_sharded, c5_sharded : BASELINE configs 3, 4 and 5 with the pair set FIXED.  N = 1: the config on this GPU and one
@@ -31,6 +32,10 @@ Besides `value` (device-resident rate, SURVEY.md 8(d) and the driver's contract;
   roofline, cpu_baseline : as the contract asks (roofline.frac from SURVEY 8(d)'s algorithmic bytes);
   shares               : LAST key -- the compact strong-scaling table of c3 / c4 / c5 (tools/bench_lib.shares_summary).
 A failed gate anywhere in the line makes EVERY rank exit non-zero (after the line is printed, with `gates_failed` in it).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0's share: what `PairBatch.fetch` returns, and
+the P x P score matrix after the all-gather) as DIR/<name>.npy, float64 / float32, at most 64 MB in all; see dump_outputs().
+The inputs are a seeded synthetic family, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -87,16 +92,53 @@ def spawn_ranks(n_gpus: int) -> int:
     return 0
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, aln, pairs, matrix):
+    """The last timed step's outputs as <out_dir>/<name>.npy: every field of the per-pair records (float64, one row per pair;
+    integer fields are exact in float64), the alignment rows (float32 [rows, 2, stride], -1 past each pair's aln_len, where
+    the fetched array holds no data), the pair (i, j) of each row and the P x P matrix.  When the rows would exceed the
+    budget, a fixed sample of them (seed 0, in pair order) is written; pair_index.npy holds the rows written."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    fields = res.dtype.names
+    per_pair = sum(8 * int(np.prod(res.dtype[f].shape or (1,))) for f in fields)
+    stride = aln.shape[2]
+    row_bytes = per_pair + 8 * 2 + 8 + 4 * 2 * stride      # fields + pairs + pair_index + alignment rows
+    budget_rows = (DUMP_BUDGET_BYTES - matrix.nbytes - (64 << 10)) // row_bytes     # (64 KB: the .npy headers)
+    n = len(res)
+    if n <= budget_rows:
+        rows = np.arange(n)
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=int(budget_rows), replace=False))
+    arrays = {f: res[f][rows].astype(np.float64) for f in fields}
+    lens = res["aln_len"][rows].astype(np.int64)
+    filled = np.arange(stride)[None, None, :] < lens[:, None, None]
+    arrays["alignment"] = np.where(filled, aln[rows], -1).astype(np.float32)
+    arrays["pairs"] = np.asarray(pairs)[rows].astype(np.float64)
+    arrays["pair_index"] = rows.astype(np.float64)
+    arrays["matrix"] = np.asarray(matrix, dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(out_dir / f"{name}.npy", arr)
+    return {"dir": str(out_dir), "rows": int(len(rows)), "of_rows": int(n),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="headline", choices=["headline", "c2", "c3", "c4", "c5"])
-    ap.add_argument("--repeats", type=int, default=10, help="how often the timed region of --steps steps is repeated (the line reports the median run)")
+    ap.add_argument("--repeats", type=int, default=1, help="how often the timed region of --steps steps is repeated (the line reports the median run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="the contract's line only: no transfers / sharded configs / consumers")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process starts the N ranks itself (it never touches a GPU)
@@ -164,6 +206,8 @@ def main():
         matrix = engine.assemble_matrix(pairs, head_scores, num)
 
     extras = {}
+    if rank == 0 and args.dump_outputs:
+        extras["dumped_outputs"] = dump_outputs(args.dump_outputs, res, aln, pairs[mine], matrix)
     gated = not args.no_cpu_baseline
     orc = None
     if gated and rank == 0:
