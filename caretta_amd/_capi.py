@@ -115,6 +115,9 @@ SIGNATURES = {
     "cr_neighbor_joining": [_vp, _i64, _vp, _vp],
     "cr_neighbor_joining_device": [_vp, _vp, _i64, _vp, _vp],
     "cr_assemble_matrix": [_vp, _vp, _i64, _i64, _vp],
+    "cr_count_matrix": [_vp, _vp, _vp, _i64, _i64, _vp],
+    "cr_braycurtis": [_vp, _vp, _i64, _vp, _i64, _i64, _vp],
+    "cr_shapemer_distance_matrix": [_vp, _vp, _vp, _i64, _i64, _vp],
 }
 
 _lib = None

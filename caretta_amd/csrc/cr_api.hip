@@ -1880,3 +1880,4 @@ int cr_batch_destroy(cr_batch* b) {
 #include "cr_explicit_batch.h"
 #include "cr_nj_device.h"
 #include "cr_multi.h"
+#include "cr_shapemer.h"

@@ -73,6 +73,7 @@ struct Calibration {
     bool multi_numa = false;         // CARETTA_MULTI_NUMA=1: pin each device's host thread to the CPUs of the device's NUMA node
     std::string rccl_lib;            // CARETTA_RCCL_LIB
     long long cache_mb = 0;          // CARETTA_CACHE_MB
+    int shapemer_form = 0;           // CARETTA_SHAPEMER_FORM=1..3: the Bray-Curtis packing (u8 sad, u16 min, u32 sad) when it holds the counts
     bool no_cache = false;           // CARETTA_NO_CACHE
 
     static StripPlanEnv plan_from(const char* name, int fields) {
@@ -125,6 +126,7 @@ struct Calibration {
         c.multi_numa = env_ll("CARETTA_MULTI_NUMA", 0) == 1;
         if (const char* e = env_str("CARETTA_RCCL_LIB")) c.rccl_lib = e;
         c.cache_mb = env_ll("CARETTA_CACHE_MB", 0);
+        c.shapemer_form = (int)env_ll("CARETTA_SHAPEMER_FORM", 0);
         c.no_cache = env_set("CARETTA_NO_CACHE");
         return c;
     }

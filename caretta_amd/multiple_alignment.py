@@ -1,6 +1,7 @@
 """Host-side mirror of the pairwise-alignment surface of the reference's
 ``caretta/multiple_alignment.py``: ``SequenceBase`` (:109-127), ``Protein`` (:312-387),
-``MultipleAlignment`` (:148-309), ``tm_score`` (:59-70), ``make_rmsd_coverage_tm_matrix`` (:1000-1055).
+``MultipleAlignment`` (:148-309), ``tm_score`` (:59-70), ``make_rmsd_coverage_tm_matrix`` (:1000-1055),
+``make_count_matrix`` (:130-136) and ``braycurtis`` (:139-145).
 
 The O(P^2) pair loop of ``make_pairwise_matrix`` (:158-170) runs as one batched launch sequence on
 the GPU (``engine.PairBatch``); everything numeric goes through the C ABI.
@@ -683,6 +684,20 @@ class MultipleAlignment:
                                                 gamma_weight, score_function_params, mean_function_params)
         return self.alignment
 
+    def make_shapemer_distance_matrix(self, shapemer_indices, alphabet_size: int) -> np.ndarray:
+        """The fast guide-tree matrix of align_from_structure_files (full=False, multiple_alignment.py:496-508):
+        ``braycurtis(make_count_matrix(shapemer_indices, alphabet_size), same)`` in one call, the counts never formed
+        in f64.  ``shapemer_indices``: one integer array per sequence, in ``self.sequences`` order (what geometricus'
+        ``map_protein_to_shapemer_indices`` gives per protein).  The result feeds ``multiple_align`` unchanged."""
+        if len(shapemer_indices) != len(self.sequences):
+            raise ValueError(f"{len(shapemer_indices)} index lists for {len(self.sequences)} sequences")
+        idx, offsets = _index_lists(shapemer_indices)
+        num = len(offsets) - 1
+        out = np.empty((num, num), dtype=np.float64)
+        check(_capi.load().cr_shapemer_distance_matrix(default_context()._h, ptr(idx), ptr(offsets), num,
+                                                        _alphabet_size(alphabet_size), ptr(out)))
+        return out
+
     def to_sequence_alignment(self, alignment=None):
         """multiple_alignment.py:287-297"""
         alignment = self.alignment if alignment is None else alignment
@@ -708,6 +723,55 @@ def alignment_to_numpy(alignment: typing.Dict[str, str]) -> typing.Dict[str, np.
     for name, gapped in alignment.items():
         present = np.frombuffer(str(gapped).encode("ascii", "replace"), dtype=np.uint8) != ord("-")
         out[name] = np.where(present, np.cumsum(present) - 1, -1)
+    return out
+
+
+def _alphabet_size(alphabet_size) -> int:
+    k = int(alphabet_size)
+    if k != alphabet_size or k < 1:
+        raise ValueError(f"alphabet_size must be a positive integer, got {alphabet_size!r}")
+    return k
+
+
+def _index_lists(residues_list):
+    """Index lists -> CSR (int32 values, int64 offsets).  Values that do not fit int32 are rejected here; the kernels
+    reject the remaining ones outside [0, alphabet_size)."""
+    lists = [np.asarray(r) for r in residues_list]
+    for r in lists:
+        if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
+            raise ValueError("each index list must be a 1-D array of integers")
+    offsets = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([r.size for r in lists], out=offsets[1:])
+    flat = np.concatenate([r.astype(np.int64, copy=False) for r in lists]) if offsets[-1] else np.zeros(0, np.int64)
+    if flat.size and (flat.min() < 0 or flat.max() > np.iinfo(np.int32).max):
+        raise ValueError("a shapemer index lies outside [0, alphabet_size)")
+    return np.ascontiguousarray(flat, dtype=np.int32), offsets
+
+
+def make_count_matrix(residues_list, alphabet_size: int) -> np.ndarray:
+    """(len(residues_list), alphabet_size) f64 counts of each list's indices (multiple_alignment.py:130-136,
+    :390-396), histogrammed on the device.  An index outside [0, alphabet_size) raises ValueError."""
+    idx, offsets = _index_lists(residues_list)
+    num = len(offsets) - 1
+    k = _alphabet_size(alphabet_size)
+    out = np.empty((num, k), dtype=np.float64)
+    check(_capi.load().cr_count_matrix(default_context()._h, ptr(idx), ptr(offsets), num, k, ptr(out)))
+    return out
+
+
+def braycurtis(counts_1, counts_2) -> np.ndarray:
+    """Bray-Curtis distances between all rows of two count matrices (multiple_alignment.py:139-145):
+    ``sum|a - b| / sum(a + b)``, bit-identical to the reference for integer counts.  ``counts_1 is counts_2`` (the
+    guide-tree case) computes one triangle and mirrors it.  Negative, non-integer or NaN counts and a pair of rows
+    without counts (0 / 0) raise ValueError."""
+    same = counts_1 is counts_2
+    a = f64(counts_1)
+    b = a if same else f64(counts_2)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("counts_1 and counts_2 must be 2-D with equal width")
+    out = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
+    check(_capi.load().cr_braycurtis(default_context()._h, ptr(a), a.shape[0], ptr(b), b.shape[0], a.shape[1],
+                                     ptr(out)))
     return out
 
 

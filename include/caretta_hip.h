@@ -354,6 +354,27 @@ int cr_neighbor_joining_device(cr_context *ctx, const double *D, int64_t P, uint
 /* scatter per-pair scores into the symmetric P x P matrix (multiple_alignment.py:161-169) */
 int cr_assemble_matrix(const int32_t *pairs, const double *scores, int64_t npairs, int64_t P, double *M);
 
+/* ---- the fast guide tree: shapemer counts and Bray-Curtis distances (align_from_structure_files with full=False,
+ * multiple_alignment.py:496-508) ----------------------------------------------------------------------------------
+ * Index lists are CSR: the indices of list i are idx[offsets[i] .. offsets[i+1]), int32 values in [0, alphabet_size);
+ * offsets has num_lists + 1 entries, starting at 0.  An index outside [0, alphabet_size) is CR_ERR_ARGUMENT.
+ * Distances are exact integer sums and one correctly rounded f64 division: equal to the reference's bit for bit.
+ * A pair of rows without counts (0 / 0; the reference raises ZeroDivisionError) is CR_ERR_ARGUMENT. */
+/* make_count_matrix(residues_list, alphabet_size)                     multiple_alignment.py:130-136, :390-396
+ * out: f64 (num_lists, alphabet_size). */
+int cr_count_matrix(cr_context *ctx, const int32_t *idx, const int64_t *offsets, int64_t num_lists, int64_t alphabet_size,
+                    double *out);
+/* braycurtis(counts_1, counts_2)                                       multiple_alignment.py:139-145
+ * counts_1 (P, K), counts_2 (M, K) f64, out (P, M).  Counts must be non-negative integers with row sums below 2^31
+ * (negative, non-integer or NaN counts: CR_ERR_ARGUMENT).  counts_1 == counts_2 with P == M computes the upper
+ * triangle and mirrors it. */
+int cr_braycurtis(cr_context *ctx, const double *counts_1, int64_t P, const double *counts_2, int64_t M, int64_t K,
+                  double *out);
+/* braycurtis(make_count_matrix(lists, K), same) fused: index lists -> P x P distances (multiple_alignment.py:503-507),
+ * the f64 counts are never formed.  Every list must be non-empty (its diagonal entry would be 0 / 0). */
+int cr_shapemer_distance_matrix(cr_context *ctx, const int32_t *idx, const int64_t *offsets, int64_t num_lists,
+                                int64_t alphabet_size, double *out);
+
 #ifdef __cplusplus
 }
 #endif
