@@ -118,6 +118,10 @@ SIGNATURES = {
     "cr_count_matrix": [_vp, _vp, _vp, _i64, _i64, _vp],
     "cr_braycurtis": [_vp, _vp, _i64, _vp, _i64, _i64, _vp],
     "cr_shapemer_distance_matrix": [_vp, _vp, _vp, _i64, _i64, _vp],
+    "cr_structure_features": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "cr_structure_shapemer_distance_matrix": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "cr_superpose_core_atoms": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp],
+    "cr_superpose_members_atoms": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64],
 }
 
 _lib = None

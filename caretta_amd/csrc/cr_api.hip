@@ -1881,3 +1881,4 @@ int cr_batch_destroy(cr_batch* b) {
 #include "cr_nj_device.h"
 #include "cr_multi.h"
 #include "cr_shapemer.h"
+#include "cr_features.h"

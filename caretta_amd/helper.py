@@ -129,3 +129,55 @@ def normalize(numbers) -> np.ndarray:
     numbers = np.asarray(numbers, dtype=np.float64)
     lo, hi = np.min(numbers), np.max(numbers)
     return (numbers - lo) / (hi - lo)
+
+
+# the stand-in tensor width of align_from_structure_files: 10 columns, alphabet of 2^10 shapemers
+STANDIN_WIDTH = 10
+
+
+def _pack_coordinates(coordinates_list):
+    lists = [np.ascontiguousarray(x, dtype=np.float64) for x in coordinates_list]
+    for x in lists:
+        if x.ndim != 2 or x.shape[1] != 3 or x.shape[0] == 0:
+            raise ValueError("each structure must be a non-empty (L, 3) array of coordinates")
+    offsets = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([x.shape[0] for x in lists], out=offsets[1:])
+    return np.ascontiguousarray(np.concatenate(lists, axis=0)), offsets
+
+
+def _split(flat, offsets):
+    return [flat[offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
+
+
+def structure_features(coordinates_list, width: int = STANDIN_WIDTH):
+    """local_shape_descriptor(x, width) of every structure and its stand-in shapemer indices, in one device launch
+    (cr_structure_features).  Returns (tensors: list of (L, width) float64, indices: list of (L,) int32).  The index of
+    a residue is its row thresholded at 0.5 (a C-alpha distance of 10 A) read as a width-bit number, first column most
+    significant: its position in itertools.product([0, 1], repeat=width), the key order of the reference
+    (multiple_alignment.py:503).  NOT geometricus' shapemers: outside the parity contract."""
+    from .engine import default_context
+    coords, offsets = _pack_coordinates(coordinates_list)
+    width = int(width)
+    tensors = np.empty((coords.shape[0], max(width, 0)), dtype=np.float64)
+    idx = np.empty(coords.shape[0], dtype=np.int32)
+    check(_capi.load().cr_structure_features(default_context()._h, ptr(coords), ptr(offsets), len(offsets) - 1, width,
+                                             ptr(tensors), ptr(idx)))
+    return _split(tensors, offsets), _split(idx, offsets)
+
+
+def structure_shapemer_distance_matrix(coordinates_list, width: int = STANDIN_WIDTH, return_features: bool = False):
+    """The fast guide-tree matrix from coordinates: braycurtis(make_count_matrix(indices, 2^width), same) on the
+    stand-in shapemers of structure_features, in one call (cr_structure_shapemer_distance_matrix; the indices never
+    leave the device).  return_features: also (tensors, indices) as structure_features returns them."""
+    from .engine import default_context
+    coords, offsets = _pack_coordinates(coordinates_list)
+    width, num = int(width), len(offsets) - 1
+    out = np.empty((num, num), dtype=np.float64)
+    tensors = np.empty((coords.shape[0], max(width, 0)), dtype=np.float64) if return_features else None
+    idx = np.empty(coords.shape[0], dtype=np.int32) if return_features else None
+    check(_capi.load().cr_structure_shapemer_distance_matrix(
+        default_context()._h, ptr(coords), ptr(offsets), num, width, None if tensors is None else ptr(tensors),
+        None if idx is None else ptr(idx), ptr(out)))
+    if return_features:
+        return out, _split(tensors, offsets), _split(idx, offsets)
+    return out

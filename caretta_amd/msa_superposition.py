@@ -185,3 +185,47 @@ def make_rmsd_coverage_tm_matrix(alignment, proteins, superpose_first: bool = Tr
     if np.isnan(rmsd).any():
         raise AssertionError("a pair of rows shares fewer than 3 positions (reference: assert len(pos_1) >= 3)")
     return rmsd, coverage, tm
+
+
+def _pack_atoms(msa_rows, atoms_list, ca_rows_list):
+    atoms = np.ascontiguousarray(np.vstack([f64(a).reshape(-1, 3) for a in atoms_list]))
+    atom_offsets = np.zeros(len(atoms_list) + 1, dtype=np.int64)
+    np.cumsum([len(a) for a in atoms_list], out=atom_offsets[1:])
+    ca_rows = np.ascontiguousarray(np.concatenate([np.asarray(r) for r in ca_rows_list]), dtype=np.int32)
+    offsets = np.zeros(len(ca_rows_list) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in ca_rows_list], out=offsets[1:])
+    msa = np.ascontiguousarray(np.array([np.asarray(r) for r in msa_rows]), dtype=np.int32)
+    if not (len(msa_rows) == len(atoms_list) == len(ca_rows_list)) or msa.ndim != 2:
+        raise ValueError("one alignment row, one atom array and one C-alpha row map per structure")
+    return msa, atoms, atom_offsets, ca_rows, offsets
+
+
+def superpose_core_atoms(msa_rows, atoms_list, ca_rows_list, ref, core_indices):
+    """The moves of write_superposed_pdbs_core (multiple_alignment.py:639-689): structure i has alignment row
+    msa_rows[i], atoms atoms_list[i] (N_i, 3) and its residues' C-alpha rows ca_rows_list[i]; every structure is fitted
+    onto structure `ref` over the core columns on its C-alpha atoms, exactly as superpose_core fits them, and all of its
+    atoms are moved (cr_superpose_core_atoms, one launch).  Returns the moved atoms, one array per structure."""
+    msa, atoms, atom_offsets, ca_rows, offsets = _pack_atoms(msa_rows, atoms_list, ca_rows_list)
+    core = np.ascontiguousarray(core_indices, dtype=np.int32)
+    moved = np.empty_like(atoms)
+    check(_capi.load().cr_superpose_core_atoms(default_context()._h, ptr(atoms), ptr(atom_offsets), ptr(ca_rows), ptr(offsets),
+                                               len(msa), ptr(msa), msa.shape[1], ptr(core), len(core), int(ref), ptr(moved)))
+    return [moved[atom_offsets[i]:atom_offsets[i + 1]].copy() for i in range(len(msa))]
+
+
+def superpose_members_atoms(msa_rows, atoms_list, ca_rows_list, ref, which):
+    """One group of write_superposed_pdbs_references (multiple_alignment.py:786-853): the structures `which` (indices)
+    fitted onto structure `ref` as it is in atoms_list, over the columns each shares with it, all of their atoms moved
+    (cr_superpose_members_atoms, one launch).  Returns every structure's atoms, the others unchanged.  A listed structure
+    that shares 3 or fewer columns with `ref` is an AssertionError, as in the reference (:826)."""
+    msa, atoms, atom_offsets, ca_rows, offsets = _pack_atoms(msa_rows, atoms_list, ca_rows_list)
+    which = np.ascontiguousarray(which, dtype=np.int32)
+    try:
+        check(_capi.load().cr_superpose_members_atoms(default_context()._h, ptr(atoms), ptr(atom_offsets), ptr(ca_rows),
+                                                      ptr(offsets), len(msa), ptr(msa), msa.shape[1], int(ref), ptr(which),
+                                                      len(which)))
+    except ValueError as e:
+        if "3 or fewer" in str(e):
+            raise AssertionError(str(e)) from None
+        raise
+    return [atoms[atom_offsets[i]:atom_offsets[i + 1]].copy() for i in range(len(msa))]

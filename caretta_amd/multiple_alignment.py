@@ -1,7 +1,8 @@
 """Host-side mirror of the pairwise-alignment surface of the reference's
 ``caretta/multiple_alignment.py``: ``SequenceBase`` (:109-127), ``Protein`` (:312-387),
 ``MultipleAlignment`` (:148-309), ``tm_score`` (:59-70), ``make_rmsd_coverage_tm_matrix`` (:1000-1055),
-``make_count_matrix`` (:130-136) and ``braycurtis`` (:139-145).
+``make_count_matrix`` (:130-136), ``braycurtis`` (:139-145), and the entry point from structure files:
+``OutputFiles`` (:85-105), ``align_from_structure_files`` (:399-593) and ``write_superposed_pdbs*`` (:596-853).
 
 The O(P^2) pair loop of ``make_pairwise_matrix`` (:158-170) runs as one batched launch sequence on
 the GPU (``engine.PairBatch``); everything numeric goes through the C ABI.
@@ -12,6 +13,7 @@ import ctypes as C
 import typing
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
+from pathlib import Path
 
 import numpy as np
 
@@ -619,6 +621,15 @@ class MultipleAlignment:
         except Exception:
             pass
 
+    def __getstate__(self):
+        """Pickling (write_class, multiple_alignment.py:558-564): the intermediate nodes of a device-resident
+        progressive_align are fetched first and the library handle is left out, so the pickle loads anywhere."""
+        if self.__dict__.get("_pending_nodes") is not None:
+            self._materialize_nodes()
+        state = dict(self.__dict__)
+        state.pop("_pending_nodes", None)
+        return state
+
     def _materialize_nodes(self):
         """Fetch the intermediate nodes of the last device-resident progressive_align and rebuild
         final_sequences / final_consensus_weights / final_alignments exactly as multiple_alignment.py:193-251 leaves them."""
@@ -786,6 +797,262 @@ def make_rmsd_coverage_tm_matrix(alignment, proteins, superpose_first: bool = Tr
     """multiple_alignment.py:1000-1055 (see caretta_amd.msa_superposition)."""
     from .msa_superposition import make_rmsd_coverage_tm_matrix as impl
     return impl(alignment, proteins, superpose_first)
+
+
+@dataclass
+class OutputFiles:
+    """Where align_from_structure_files writes (multiple_alignment.py:85-105)."""
+    output_folder: Path = Path("./caretta_results")
+    fasta_file: Path = Path("./caretta_results/result.fasta")
+    pdb_folder: Path = Path("./caretta_results/result_pdb/")
+    cleaned_pdb_folder: Path = Path("./caretta_results/cleaned_pdb")
+    matrix_folder: Path = Path("./caretta_results/result_matrix")
+    feature_file: Path = Path("./caretta_results/result_features.pkl")
+    class_file: Path = Path("./caretta_results/result_class.pkl")
+    tmp_folder: Path = Path("./caretta_results/tmp/")
+
+    @classmethod
+    def from_folder(cls, output_folder):
+        output_folder = Path(output_folder)
+        return cls(output_folder,
+                   fasta_file=output_folder / "result.fasta",
+                   pdb_folder=output_folder / "result_pdb/",
+                   cleaned_pdb_folder=output_folder / "cleaned_pdb",
+                   matrix_folder=output_folder / "result_matrix",
+                   feature_file=output_folder / "result_features.pkl",
+                   class_file=output_folder / "result_class.pkl",
+                   tmp_folder=output_folder / "tmp/")
+
+
+def _echo(verbose, message, color=None):
+    """Progress text as the reference prints it (typer.echo, optionally styled)."""
+    if not verbose:
+        return
+    import typer
+    typer.echo(message if color is None else typer.style(message, fg=color))
+
+
+def align_from_structure_files(
+        input_files: typing.Union[typing.List[str], Path, str],
+        gap_open_penalty: float = 1.0,
+        gap_extend_penalty: float = 0.01,
+        consensus_weight: bool = True,
+        full: bool = False,
+        output_folder: typing.Union[str, Path] = Path("../caretta_results"),
+        num_threads: int = 20,
+        write_fasta: bool = False,
+        write_pdb: bool = False,
+        write_features: bool = False,
+        only_dssp: bool = True,
+        write_class: bool = False,
+        write_matrix: bool = False,
+        verbose: bool = True,
+        features: typing.Optional[typing.Callable] = None,
+        alphabet_size: typing.Optional[int] = None,
+) -> typing.Tuple[MultipleAlignment, OutputFiles]:
+    """Align protein structures from files (multiple_alignment.py:399-593): the reference's steps, order and constants.
+
+    input_files: a folder, a list of .pdb / .ent / .pdb.gz files or of (file, chain) tuples, or a text file listing
+    one file per line (optionally "file, chain").  Only the first model and the chosen chain (default: the first) are
+    kept, cleaned into ``output_folder/cleaned_pdb/<stem>.pdb``; the protein is named ``<stem>``.  PDB IDs are not
+    downloaded: an input that is not an existing file or folder is a ValueError.
+
+    Features.  NOT THE REFERENCE'S unless ``features`` is given: the reference takes its tensors and shapemers from
+    geometricus, which is not used here.  By default every residue gets the stand-in descriptor
+    helper.local_shape_descriptor(coordinates, 10), and full=False groups residues by the stand-in shapemer rule
+    (helper.structure_features), both computed on the device.  Results are then outside the parity contract.
+    ``features(name, ca_coordinates, sequence) -> (tensor (L, d) float64, shapemer_indices)`` replaces both (with
+    ``alphabet_size`` the number of shapemers when full=False): with geometricus' tensors and indices this is the
+    reference's own route.
+
+    full=True builds the guide tree from all-vs-all Caretta scores (make_pairwise_matrix -> max - M), full=False from
+    Bray-Curtis distances of shapemer counts.  write_fasta / write_pdb / write_class / write_matrix write
+    result.fasta, result_pdb/<name>.pdb, result_class.pkl and result_matrix/ as the reference does.  write_features
+    (DSSP / ProDy features) is not available and raises ValueError before anything is created; only_dssp is accepted
+    and unused.  num_threads sizes the pool that parses input files (at most 16).  Returns (MultipleAlignment,
+    OutputFiles)."""
+    from . import structure_io
+    if write_features:
+        raise ValueError("write_features: aligned DSSP / ProDy feature extraction is not available in caretta_amd")
+    if features is not None and not callable(features):
+        raise TypeError("features must be a callable (name, ca_coordinates, sequence) -> (tensor, shapemer_indices)")
+    if features is not None and not full and alphabet_size is None:
+        raise ValueError("features= with full=False needs alphabet_size (the number of shapemers)")
+    files = structure_io.get_structure_files(input_files)
+    if len(files) < 2:
+        raise ValueError(f"{input_files!s}: found {len(files)} structure file(s), at least 2 are needed")
+    output_files = OutputFiles() if output_folder is None else OutputFiles.from_folder(Path(output_folder))
+    output_files.output_folder.mkdir(parents=True, exist_ok=True)
+    output_files.cleaned_pdb_folder.mkdir(exist_ok=True)
+    pdb_files = structure_io.parse_protein_files_and_clean(files, output_files.cleaned_pdb_folder, num_threads)
+    _echo(verbose, f"Found {len(pdb_files)} structure files")
+    names = [structure_io.structure_stem(f) for f in pdb_files]
+    calphas = [helper.read_calpha_pdb(f) for f in pdb_files]
+    num = len(names)
+    distances = np.array([[0, 1], [1, 0]])
+    if features is not None:
+        tensors, indices = [], []
+        for name, (xyz, seq) in zip(names, calphas):
+            t, idx = features(name, xyz, seq)
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if t.ndim != 2 or t.shape[0] != len(xyz):
+                raise ValueError(f"{name}: features must give one tensor row per residue ({len(xyz)}), got {t.shape}")
+            tensors.append(t)
+            indices.append(idx)
+    elif full or num == 2:
+        tensors, _ = helper.structure_features([xyz for xyz, _ in calphas], helper.STANDIN_WIDTH)
+    else:
+        # one call: stand-in tensors for the alignment and the guide-tree distances of their shapemers
+        distances, tensors, _ = helper.structure_shapemer_distance_matrix([xyz for xyz, _ in calphas], helper.STANDIN_WIDTH,
+                                                                          return_features=True)
+    _echo(verbose, f"Computed features of {num} structures")
+    proteins = [Protein(name, np.array(t), xyz, seq) for name, t, (xyz, seq) in zip(names, tensors, calphas)]
+    msa_class = MultipleAlignment(proteins)
+    score_function_params = dict(flexible=False, gamma_tensor=7., gamma_coords=0.03)
+    mean_function_params = dict(flexible=False)
+    if num > 2:
+        if full:
+            distances = msa_class.make_pairwise_matrix(score_function_params=score_function_params)
+            distances = distances.max() - distances
+        elif features is not None:
+            distances = msa_class.make_shapemer_distance_matrix(indices, alphabet_size)
+    if write_matrix:
+        _echo(verbose, "Writing guide tree distance matrix...")
+        Path(output_files.matrix_folder).mkdir(exist_ok=True)
+        helper.write_distance_matrix(names, distances, output_files.matrix_folder / "distance_matrix_guide_tree.txt")
+    msa_class.pairwise_distance_matrix = distances
+    alignment = msa_class.multiple_align(distances, gap_open_penalty=gap_open_penalty, gap_extend_penalty=gap_extend_penalty,
+                                         consensus_weight=float(consensus_weight), gamma_weight=1.,
+                                         score_function_params=score_function_params,
+                                         mean_function_params=mean_function_params)
+    if any((write_fasta, write_pdb, write_class, write_matrix)):
+        _echo(verbose, "Writing files...")
+    if write_fasta:
+        msa_class.write_alignment(output_files.fasta_file)
+        _echo(verbose, f"FASTA file: {output_files.fasta_file}")
+    if write_pdb:
+        Path(output_files.pdb_folder).mkdir(exist_ok=True)
+        write_superposed_pdbs(output_files.cleaned_pdb_folder, alignment, output_files.pdb_folder, verbose=verbose)
+        _echo(verbose, f"Superposed PDB files: {output_files.pdb_folder}")
+    if write_class:
+        import pickle
+        with open(output_files.class_file, "wb") as f:
+            pickle.dump(msa_class, f)
+        _echo(verbose, f"Class file: {output_files.class_file}")
+    if write_matrix:
+        Path(output_files.matrix_folder).mkdir(exist_ok=True)
+        rmsd, coverage, tm = make_rmsd_coverage_tm_matrix(alignment, msa_class.sequences, superpose_first=False)
+        for values, stem in ((rmsd, "rmsd"), (coverage, "coverage"), (tm, "tm")):
+            helper.write_distance_matrix(names, values, output_files.matrix_folder / f"{stem}.txt")
+        _echo(verbose, f"Distance matrix files in: {output_files.matrix_folder}")
+    return msa_class, output_files
+
+
+def _core_columns(alignment, gap=-1):
+    rows = np.array([np.asarray(alignment[n]) for n in alignment])
+    return np.flatnonzero((rows != gap).all(axis=0))
+
+
+def _read_atoms(folder, names):
+    from . import structure_io
+    return [structure_io.read_pdb_atoms(Path(folder) / f"{name}.pdb") for name in names]
+
+
+def write_superposed_pdbs(cleaned_pdb_folder, alignment, output_pdb_folder, verbose: bool = False):
+    """Superpose the cleaned structures by the alignment and write them to output_pdb_folder/<name>.pdb
+    (multiple_alignment.py:596-637): on the gap-free core when it spans at least half of the alignment, otherwise on a
+    set of reference structures."""
+    reference_name = sorted(alignment.keys(), key=lambda x: sum(1 for a in alignment[x] if a != -1), reverse=True)[0]
+    output_pdb_folder = Path(output_pdb_folder)
+    output_pdb_folder.mkdir(exist_ok=True)
+    core = _core_columns(alignment)
+    _echo(verbose, f"{len(core)} core positions in alignment of length {len(alignment[reference_name])}")
+    if len(core) < len(alignment[reference_name]) // 2:
+        _echo(verbose, "Core indices are < half of alignment length, superposing using reference structures instead", "red")
+        write_superposed_pdbs_references(Path(cleaned_pdb_folder), alignment, output_pdb_folder, verbose=verbose)
+    else:
+        write_superposed_pdbs_core(Path(cleaned_pdb_folder), alignment, reference_name, output_pdb_folder)
+
+
+def write_superposed_pdbs_core(cleaned_pdb_folder, alignment, reference_name, output_pdb_folder):
+    """Every structure fitted onto the reference over the gap-free columns on its C-alpha atoms, all atoms moved, in one
+    launch (multiple_alignment.py:639-689; msa_superposition.superpose_core_atoms)."""
+    from . import structure_io
+    from .msa_superposition import superpose_core_atoms
+    names = list(alignment)
+    structures = _read_atoms(cleaned_pdb_folder, names)
+    moved = superpose_core_atoms([alignment[n] for n in names], [s.coords for s in structures],
+                                 [s.ca_rows for s in structures], names.index(reference_name), _core_columns(alignment))
+    for name, s, xyz in zip(names, structures, moved):
+        structure_io.write_pdb_atoms(Path(output_pdb_folder) / f"{name}.pdb", s, xyz)
+
+
+def _fit_group(alignment, names, structures, target, ref_name, members):
+    """Atoms of `members` fitted onto `target` (the reference's atoms as they are to be fitted on) over the columns each
+    shares with ref_name: the target goes in as one more structure with ref_name's alignment row, so a member may be
+    ref_name itself (the reference refits its own file, :817-849)."""
+    from .msa_superposition import superpose_members_atoms
+    index = {n: i for i, n in enumerate(names)}
+    rows = [alignment[n] for n in names] + [alignment[ref_name]]
+    atoms = [s.coords for s in structures] + [target.coords]
+    ca_rows = [s.ca_rows for s in structures] + [target.ca_rows]
+    return superpose_members_atoms(rows, atoms, ca_rows, len(names), [index[m] for m in members])
+
+
+def write_superposed_pdbs_reference(cleaned_pdb_folder, alignment, reference_name, output_pdb_folder, verbose=True):
+    """Every structure fitted onto one reference over the positions the two share, all atoms moved
+    (multiple_alignment.py:692-738).  The reference is written as it is; a structure sharing 3 or fewer positions with
+    it is skipped."""
+    from . import structure_io
+    names = list(alignment)
+    structures = _read_atoms(cleaned_pdb_folder, names)
+    ref = names.index(reference_name)
+    structure_io.write_pdb_atoms(Path(output_pdb_folder) / f"{reference_name}.pdb", structures[ref], structures[ref].coords)
+    aln_ref = np.asarray(alignment[reference_name])
+    members = []
+    for name in names:
+        if name == reference_name:
+            continue
+        if np.count_nonzero((aln_ref != -1) & (np.asarray(alignment[name]) != -1)) <= 3:
+            _echo(verbose, f"Not enough common positions to superpose {reference_name} and {name}")
+            continue
+        members.append(name)
+    moved = _fit_group(alignment, names, structures, structures[ref], reference_name, members)
+    for name in members:
+        structure_io.write_pdb_atoms(Path(output_pdb_folder) / f"{name}.pdb", structures[names.index(name)],
+                                     moved[names.index(name)])
+
+
+def write_superposed_pdbs_references(cleaned_pdb_folder, alignment, output_pdb_folder, minimum_coverage=50, verbose=False):
+    """Every structure fitted onto the reference structure chosen for it (get_reference_structures), all atoms moved,
+    one launch per reference (multiple_alignment.py:786-853).  Each reference is fitted on as it was written to
+    output_pdb_folder, re-read from there as the reference re-parses it.  references.txt (verbose, more than one
+    reference) and missing.txt (structures no reference covers) as the reference writes them."""
+    from . import structure_io
+    from .msa_superposition import get_reference_structures
+    output_pdb_folder = Path(output_pdb_folder)
+    first, groups, no_aligning = get_reference_structures(alignment, minimum_coverage)
+    if verbose:
+        _echo(verbose, "Reference structure(s): " + " ".join(groups.keys()))
+        if len(groups) > 1:
+            with open(output_pdb_folder / "references.txt", "w") as f:
+                for r in groups:
+                    f.write(r + "".join(f"\t{k}" for k in groups[r]) + "\n")
+    names = list(alignment)
+    structures = _read_atoms(cleaned_pdb_folder, names)
+    first_structure = structures[names.index(first)]
+    structure_io.write_pdb_atoms(output_pdb_folder / f"{first}.pdb", first_structure, first_structure.coords)
+    for reference_name, members in groups.items():
+        target = structure_io.read_pdb_atoms(output_pdb_folder / f"{reference_name}.pdb")
+        moved = _fit_group(alignment, names, structures, target, reference_name, members)
+        for name in members:
+            i = names.index(name)
+            structure_io.write_pdb_atoms(output_pdb_folder / f"{name}.pdb", structures[i], moved[i])
+    if len(no_aligning):
+        with open(output_pdb_folder / "missing.txt", "w") as f:
+            f.write("\n".join(no_aligning))
+        _echo(verbose, f"Could not superpose {len(no_aligning)} structures as there are not enough aligning residues: "
+                       f"{no_aligning}")
 
 
 def __getattr__(name):

@@ -136,3 +136,25 @@ def pack(structures: List[Structure]):
     coords = np.ascontiguousarray(np.vstack([s.coordinates for s in structures]), dtype=np.float64)
     tensors = np.ascontiguousarray(np.vstack([s.tensors for s in structures]), dtype=np.float64)
     return coords, tensors, offsets
+
+
+def write_pdb_family(structures: List[Structure], folder) -> list:
+    """Write a family as PDB files ``folder/<name>.pdb``: per residue N, CA, C and O (the N / C / O positions are
+    fabricated around each C-alpha at bond-like distances; only the C-alpha atoms enter any fit).  Returns the paths."""
+    from pathlib import Path
+    folder = Path(folder)
+    folder.mkdir(parents=True, exist_ok=True)
+    around = {"N": (-1.20, 0.60, 0.30), "CA": (0.0, 0.0, 0.0), "C": (1.20, 0.55, -0.25), "O": (1.55, 1.70, -0.40)}
+    paths = []
+    for s in structures:
+        lines, serial = [], 1
+        for i, (x, aa) in enumerate(zip(s.coordinates, s.sequence)):
+            res = {"A": "ALA", "G": "GLY"}.get(aa, "ALA")
+            for atom, d in around.items():
+                lines.append(f"ATOM  {serial:5d}  {atom:<3} {res} A{i + 1:4d}    {x[0] + d[0]:8.3f}{x[1] + d[1]:8.3f}"
+                             f"{x[2] + d[2]:8.3f}  1.00  0.00           {atom[0]}")
+                serial += 1
+        path = folder / f"{s.name}.pdb"
+        path.write_text("\n".join(lines) + "\nTER\nEND\n")
+        paths.append(path)
+    return paths

@@ -375,6 +375,37 @@ int cr_braycurtis(cr_context *ctx, const double *counts_1, int64_t P, const doub
 int cr_shapemer_distance_matrix(cr_context *ctx, const int32_t *idx, const int64_t *offsets, int64_t num_lists,
                                 int64_t alphabet_size, double *out);
 
+/* ---- structure files: the front end and the all-atom moves of align_from_structure_files (multiple_alignment.py:399-593)
+ * The reference takes tensors and shapemers from geometricus (:479-488, :503-505); these use the stand-in of
+ * helper.local_shape_descriptor instead, so results from them are outside the parity contract.
+ * coords f64[total, 3] + offsets i64[P+1] (strictly increasing from 0, no empty structure) as in cr_batch_create; width
+ * in [1, 16]; non-finite coordinates are CR_ERR_ARGUMENT. */
+/* per-residue tensors and stand-in shapemers of all P structures, one launch.
+ * tensors_out f64[total, width]: equal to helper.local_shape_descriptor(coords_s, width) bit for bit (offsets -2, +2,
+ * -3, +3, ... clipped to the structure; d / (d + 10)).  idx_out i32[total]: sum_b [tensors[r, b] >= 0.5] 2^(width-1-b),
+ * the index of the binarised row in itertools.product([0, 1], repeat=width) (the key order of :503). */
+int cr_structure_features(cr_context *ctx, const double *coords, const int64_t *offsets, int64_t num_structures,
+                          int64_t width, double *tensors_out, int32_t *idx_out);
+/* the fast guide tree from coordinates (:496-508 with the stand-in shapemers): the indices of cr_structure_features go
+ * straight into the histogram and Bray-Curtis kernels of cr_shapemer_distance_matrix (alphabet_size = 2^width), whose
+ * result this equals bit for bit.  tensors_out and idx_out may be null; out f64[P, P]. */
+int cr_structure_shapemer_distance_matrix(cr_context *ctx, const double *coords, const int64_t *offsets,
+                                          int64_t num_structures, int64_t width, double *tensors_out, int32_t *idx_out,
+                                          double *out);
+/* write_superposed_pdbs_core (:639-689): cr_superpose_core's fit on C-alpha rows, its R, t applied to every atom.
+ * atoms f64[atom_offsets[P], 3]; ca_rows i32[offsets[P]]: the row of residue i of structure s among that structure's
+ * atoms; offsets i64[P+1] count residues, the alignment's indices refer to them.  atoms_out: every atom moved; its
+ * C-alpha rows equal cr_superpose_core's output on atoms[ca_rows] bit for bit. */
+int cr_superpose_core_atoms(cr_context *ctx, const double *atoms, const int64_t *atom_offsets, const int32_t *ca_rows,
+                            const int64_t *offsets, int64_t num_structures, const int32_t *msa, int64_t width,
+                            const int32_t *core, int64_t ncore, int64_t ref, double *atoms_out);
+/* one group of write_superposed_pdbs_references (:786-853), in place: the structures which[nwhich] fitted onto `ref`
+ * as cr_superpose_members fits them, every one of their atoms moved.  CR_ERR_ARGUMENT if one shares 3 or fewer
+ * columns with `ref` (:826); atoms is then unchanged. */
+int cr_superpose_members_atoms(cr_context *ctx, double *atoms, const int64_t *atom_offsets, const int32_t *ca_rows,
+                               const int64_t *offsets, int64_t num_structures, const int32_t *msa, int64_t width,
+                               int64_t ref, const int32_t *which, int64_t nwhich);
+
 #ifdef __cplusplus
 }
 #endif
