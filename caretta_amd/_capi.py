@@ -122,6 +122,7 @@ SIGNATURES = {
     "cr_structure_shapemer_distance_matrix": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "cr_superpose_core_atoms": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp],
     "cr_superpose_members_atoms": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64],
+    "cr_dssp_features": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -1882,3 +1882,4 @@ int cr_batch_destroy(cr_batch* b) {
 #include "cr_multi.h"
 #include "cr_shapemer.h"
 #include "cr_features.h"
+#include "cr_dssp.h"

@@ -1061,3 +1061,26 @@ def __getattr__(name):
     if hasattr(msa_superposition, name):
         return getattr(msa_superposition, name)
     raise AttributeError(name)
+
+
+def get_aligned_features(alignment, cleaned_pdb_folder, dssp_dir, num_threads, only_dssp: bool = True, gap=-1
+                         ) -> typing.Tuple[typing.List[str], typing.Dict[str, np.ndarray]]:
+    """multiple_alignment.py:855-893: the DSSP features of every aligned protein (feature_extraction.get_features_multiple,
+    one device pass) laid out on the alignment's columns.  Returns (names, {key: (P, alignment_length) float64}), NaN at
+    gaps; "secondary" is left out, as there.  Files are cleaned_pdb_folder / "<name>.pdb".  only_dssp=False raises
+    ValueError (GNM / ANM and residue depth are not available).  The features are not mkdssp's."""
+    from . import feature_extraction
+    names = list(alignment.keys())
+    pdb_files = [Path(cleaned_pdb_folder) / f"{name}.pdb" for name in names]
+    features = feature_extraction.get_features_multiple(pdb_files, str(dssp_dir), num_threads=num_threads,
+                                                        only_dssp=only_dssp, force_overwrite=True)
+    alignment_length = len(alignment[names[0]])
+    aligned_features = {}
+    for feature_name in features[0].keys():
+        if feature_name == "secondary":
+            continue
+        aligned_features[feature_name] = np.full((len(names), alignment_length), np.nan)
+        for p in range(len(names)):
+            indices = [i for i in range(alignment_length) if alignment[names[p]][i] != gap]
+            aligned_features[feature_name][p, indices] = features[p][feature_name]
+    return names, aligned_features

@@ -203,3 +203,73 @@ def write_pdb_atoms(filename, atoms: PdbAtoms, coords) -> None:
         lines[n] = line[:30] + "".join(_coordinate_field(v) for v in coords[row]) + line[54:]
     Path(filename).write_text("\n".join(lines) + "\n")
 
+
+# radius classes of the DSSP accessibility (cr_dssp_features): N, CA, C, O by atom name, every other heavy atom
+DSSP_RADIUS_CLASS = {"N": 0, "CA": 1, "C": 2, "O": 3}
+
+
+@dataclass
+class DsspAtoms:
+    """What DSSP needs of a (cleaned) PDB file, over the residues helper.read_calpha_pdb returns (L of them): which are
+    complete (N, CA, C and O present), the backbone and PRO flag of each complete residue, and the heavy atoms of the
+    complete residues in file order with their radius class."""
+    num_residues: int            # L: C-alpha residues
+    complete: np.ndarray         # (L,) bool
+    backbone: np.ndarray         # (R, 4, 3) float64: N, CA, C, O of the complete residues
+    is_pro: np.ndarray           # (R,) int32
+    atom_offsets: np.ndarray     # (R + 1,) int64: the heavy atoms of complete residue r
+    atoms: np.ndarray            # (A, 3) float64
+    radius_class: np.ndarray     # (A,) int32
+
+
+def _element(line: str) -> str:
+    element = line[76:78].strip() if len(line) >= 78 else ""
+    if element:
+        return element.upper()
+    name = line[12:16].strip().lstrip("0123456789")
+    return name[:1].upper()
+
+
+def read_dssp_atoms(filename) -> DsspAtoms:
+    """Residues as read_pdb_atoms selects them (first model, first chain, first altloc, HETATM MSE counted), every
+    ATOM / HETATM MSE record of those residues with altloc ' ' or 'A' assigned to its residue; hydrogens (element H or D)
+    are dropped, OXT is kept.  The first N / CA / C / O of a residue make its backbone."""
+    pdb = read_pdb_atoms(filename)
+    lines = pdb.lines
+    first = lines[pdb.atom_lines[pdb.ca_rows[0]]]
+    chain = first[21]
+    residue_of = {}
+    for i, row in enumerate(pdb.ca_rows):
+        residue_of[lines[pdb.atom_lines[row]][22:27]] = i
+    num = len(pdb.ca_rows)
+    heavy = [[] for _ in range(num)]        # (row, name) per residue, file order
+    backbone = [dict() for _ in range(num)]
+    resname = [lines[pdb.atom_lines[row]][17:20].strip() for row in pdb.ca_rows]
+    for row, n in enumerate(pdb.atom_lines):
+        line = lines[n]
+        if line[21] != chain or line[16] not in (" ", "A"):
+            continue
+        if line[:6] == "HETATM" and line[17:20].strip() != "MSE":
+            continue
+        i = residue_of.get(line[22:27])
+        if i is None or _element(line) in ("H", "D"):
+            continue
+        name = line[12:16].strip()
+        heavy[i].append((row, name))
+        if name in DSSP_RADIUS_CLASS and name not in backbone[i]:
+            backbone[i][name] = row
+    complete = np.array([len(b) == 4 for b in backbone], dtype=bool)
+    bb_rows, pro, atom_rows, classes, counts = [], [], [], [], []
+    for i in np.flatnonzero(complete):
+        bb_rows.append([backbone[i][a] for a in ("N", "CA", "C", "O")])
+        pro.append(1 if resname[i] == "PRO" else 0)
+        counts.append(len(heavy[i]))
+        for row, name in heavy[i]:
+            atom_rows.append(row)
+            classes.append(DSSP_RADIUS_CLASS.get(name, 4))
+    offsets = np.zeros(len(counts) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    bb = pdb.coords[np.array(bb_rows, dtype=np.int64).reshape(-1)].reshape(-1, 4, 3)
+    return DsspAtoms(num, complete, np.ascontiguousarray(bb), np.array(pro, dtype=np.int32), offsets,
+                     np.ascontiguousarray(pdb.coords[np.array(atom_rows, dtype=np.int64)].reshape(-1, 3)),
+                     np.array(classes, dtype=np.int32))

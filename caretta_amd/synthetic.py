@@ -158,3 +158,94 @@ def write_pdb_family(structures: List[Structure], folder) -> list:
         path.write_text("\n".join(lines) + "\nTER\nEND\n")
         paths.append(path)
     return paths
+
+
+# ideal backbone geometry (Engh & Huber): bond lengths in A, bond angles in degrees
+_BOND = {"N-CA": 1.458, "CA-C": 1.525, "C-N": 1.329, "C-O": 1.231}
+_ANGLE = {"N-CA-C": 111.2, "CA-C-N": 116.2, "C-N-CA": 121.7, "CA-C-O": 120.5}
+
+
+def _place(a, b, c, bond, angle, torsion):
+    """NeRF: the atom d with |cd| = bond, angle(b, c, d) = angle and dihedral(a, b, c, d) = torsion (degrees)."""
+    angle, torsion = np.radians(angle), np.radians(torsion)
+    bc = c - b
+    bc /= np.linalg.norm(bc)
+    n = np.cross(b - a, bc)
+    n /= np.linalg.norm(n)
+    m = np.cross(n, bc)
+    d2 = np.array([-bond * np.cos(angle), bond * np.sin(angle) * np.cos(torsion), bond * np.sin(angle) * np.sin(torsion)])
+    return c + d2[0] * bc + d2[1] * m + d2[2] * n
+
+
+def ideal_backbone(phi, psi, omega=None) -> np.ndarray:
+    """Backbone (L, 4, 3) -- N, CA, C, O per residue -- built by NeRF from per-residue phi / psi / omega in degrees (omega
+    defaults to 180) with ideal bond lengths and angles.  phi[0] is unused; O lies in the peptide plane (dihedral
+    N-CA-C-O = psi + 180)."""
+    phi = np.asarray(phi, dtype=np.float64)
+    psi = np.asarray(psi, dtype=np.float64)
+    length = len(phi)
+    omega = np.full(length, 180.0) if omega is None else np.asarray(omega, dtype=np.float64)
+    out = np.zeros((length, 4, 3))
+    out[0, 0] = (0.0, 0.0, 0.0)
+    out[0, 1] = (_BOND["N-CA"], 0.0, 0.0)
+    ang = np.radians(_ANGLE["N-CA-C"])
+    out[0, 2] = out[0, 1] + _BOND["CA-C"] * np.array([-np.cos(ang), np.sin(ang), 0.0])
+    for i in range(1, length):
+        n_, ca_, c_ = out[i - 1, 0], out[i - 1, 1], out[i - 1, 2]
+        out[i, 0] = _place(n_, ca_, c_, _BOND["C-N"], _ANGLE["CA-C-N"], psi[i - 1])
+        out[i, 1] = _place(ca_, c_, out[i, 0], _BOND["N-CA"], _ANGLE["C-N-CA"], omega[i - 1])
+        out[i, 2] = _place(c_, out[i, 0], out[i, 1], _BOND["CA-C"], _ANGLE["N-CA-C"], phi[i])
+    for i in range(length):
+        out[i, 3] = _place(out[i, 0], out[i, 1], out[i, 2], _BOND["C-O"], _ANGLE["CA-C-O"], psi[i] + 180.0)
+    return out
+
+
+def full_atom_structure(rng: np.random.Generator, length: int, side_atoms: float = 3.8):
+    """A synthetic full-atom chain for timing the DSSP path: NeRF backbone from random helix / strand / coil phi-psi runs,
+    a CB and pseudo side-chain atoms stepped outwards from it, about 4 + side_atoms heavy atoms per residue (7.8 by
+    default, a protein's average).  Returns (backbone (L, 4, 3), atoms (A, 3), radius_class (A,), atom_offsets (L + 1,),
+    is_pro (L,)): the arrays of structure_io.DsspAtoms with every residue complete."""
+    states = np.array([[-57.8, -47.0], [-139.0, 135.0], [-70.0, 140.0]])
+    phi, psi = np.empty(length), np.empty(length)
+    i = 0
+    while i < length:
+        run = int(rng.integers(4, 16))
+        s = states[int(rng.integers(0, 3))]
+        phi[i:i + run] = s[0] + rng.normal(scale=6.0, size=min(run, length - i))
+        psi[i:i + run] = s[1] + rng.normal(scale=6.0, size=min(run, length - i))
+        i += run
+    bb = ideal_backbone(phi, psi)
+    is_pro = (rng.uniform(size=length) < 0.05).astype(np.int32)
+    atoms, classes, counts = [], [], []
+    for r in range(length):
+        n_, ca, c_ = bb[r, 0], bb[r, 1], bb[r, 2]
+        cb = _place(c_, n_, ca, 1.53, 110.5, -122.6)
+        extra = int(rng.poisson(side_atoms - 1.0)) if side_atoms > 1.0 else 0
+        side = [cb]
+        for _ in range(extra):
+            step = side[-1] - ca
+            step /= np.linalg.norm(step)
+            d = step + rng.normal(scale=0.35, size=3)
+            side.append(side[-1] + 1.52 * d / np.linalg.norm(d))
+        atoms += [bb[r, 0], bb[r, 1], bb[r, 2], bb[r, 3]] + side
+        classes += [0, 1, 2, 3] + [4] * len(side)
+        counts.append(4 + len(side))
+    offsets = np.zeros(length + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    shift = rng.uniform(-50.0, 50.0, size=3)
+    rot = _random_rotation(rng)
+    bb = bb @ rot + shift
+    atoms = np.asarray(atoms) @ rot + shift
+    return (np.ascontiguousarray(bb), np.ascontiguousarray(atoms), np.array(classes, dtype=np.int32), offsets, is_pro)
+
+
+def make_full_atom_family(num: int, shortest: int, longest: int, seed: int = 20260):
+    """``num`` full_atom_structure chains of ``shortest`` .. ``longest`` residues as structure_io.DsspAtoms."""
+    from .structure_io import DsspAtoms
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(num):
+        length = int(rng.integers(shortest, longest + 1))
+        bb, atoms, classes, offsets, is_pro = full_atom_structure(rng, length)
+        out.append(DsspAtoms(length, np.ones(length, dtype=bool), bb, is_pro, offsets, atoms, classes))
+    return out

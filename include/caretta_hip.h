@@ -405,6 +405,24 @@ int cr_superpose_core_atoms(cr_context *ctx, const double *atoms, const int64_t 
 int cr_superpose_members_atoms(cr_context *ctx, double *atoms, const int64_t *atom_offsets, const int32_t *ca_rows,
                                const int64_t *offsets, int64_t num_structures, const int32_t *msa, int64_t width,
                                int64_t ref, const int32_t *which, int64_t nwhich);
+/* DSSP features of a batch of structures, standing in for the reference's external mkdssp run read through ProDy
+ * (feature_extraction.py:122-253, get_features / get_dssp_features; multiple_alignment.py:855-893 aligns them).  The
+ * definitions are DESIGN section 4.6 (Kabsch & Sander 1983 with stated choices); results are NOT mkdssp's.
+ * Per structure s: res_offsets / ca_offsets i64[P+1] count its complete residues (N, CA, C and O present) and its
+ * C-alpha positions; backbone f64[R, 4, 3] (N, CA, C, O) and is_pro i32[R] per complete residue (R = res_offsets[P]);
+ * atom_offsets i64[R+1] the heavy atoms of each complete residue in file order, atoms f64[A, 3], radius_class i32[A]
+ * (0 N 1.65, 1 CA 1.87, 2 C 1.76, 3 O 1.40, 4 other 1.80 A); sphere_points f64[num_points, 3] (num_points <= 448), the
+ * Shrake-Rupley point table, each point of weight 4 pi / num_points.  Writes, at every C-alpha position (the complete
+ * residue whose DSSP number is position + 1, zeros otherwise), out f64[14, ca_offsets[P]] in the key order
+ * NH_O_1_index, NH_O_1_energy, O_NH_1_index, O_NH_1_energy, NH_O_2_index, NH_O_2_energy, O_NH_2_index, O_NH_2_energy,
+ * acc, alpha, kappa, phi, psi, tco, and secondary_out char[ca_offsets[P]] ('H', 'E', 'B', 'G', 'I', 'T', 'S', 0 for no
+ * code, '0' for a position without a residue).  raw_angles_out f64[5, ca_offsets[P]] (may be null): alpha, kappa, phi, psi
+ * and tco before rounding, zeros where no residue maps.  CR_ERR_ARGUMENT on NaN / inf or offsets that do not add up.
+ * Launches are split so that no dispatch exceeds 2^30 work-items. */
+int cr_dssp_features(cr_context *ctx, const double *backbone, const int32_t *is_pro, const int64_t *res_offsets,
+                     const int64_t *ca_offsets, const double *atoms, const int32_t *radius_class,
+                     const int64_t *atom_offsets, int64_t num_structures, const double *sphere_points,
+                     int64_t num_points, double *out, char *secondary_out, double *raw_angles_out);
 
 #ifdef __cplusplus
 }
