@@ -1704,6 +1704,7 @@ int cr_batch_run_scores(cr_batch* b, const cr_params* params, double* d_sw_out) 
 
 int cr_batch_run_tensor_scores(cr_batch* b, const cr_params* params, double* d_sw_out) {
     CR_REQUIRE(b != nullptr && params != nullptr, "null argument");
+    CR_REQUIRE(b->d_pad <= 32, "tensor scores (flexible=True): tensor width > 32 is not supported (no staged flexible provider)");
     int rc = set_device(b->ctx);
     if (rc) return rc;
     CR_REQUIRE(gamma_ok(params->gamma_tensor), "gamma_tensor must be finite and >= 1e-290 (below that every score is exactly 1.0)");

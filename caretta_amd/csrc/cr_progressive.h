@@ -179,7 +179,7 @@ int run_tree_planned(cr_progressive* h, const std::vector<std::vector<int64_t>>&
     }
     *why = !g_cfg.staged ? "CARETTA_STAGED=0" : widest_level > 65535 ? "a tree level of more than 65535 nodes"
                                                                : "the staged scores of the widest tree level exceed a tenth of the device memory";
-    if (h->flexible && !staged) return 1;                    // (flexible=True runs on staged scores only)
+    if (!staged && (h->flexible || h->scratch.d_pad > 32)) return 1;     // (flexible=True and tensors wider than 32: staged scores only)
     if (!staged && (bound <= 3 * cr::kWave || bound > 5 * cr::kTeamWaves * cr::kWave)) return 1;     // (the four-wave team kernels: 193 .. 1280 rows)
     const int R = staged ? shape.r : (bound + cr::kTeamWaves * cr::kWave - 1) / (cr::kTeamWaves * cr::kWave);
 
@@ -374,6 +374,7 @@ static int progressive_align_impl(cr_context* ctx, const double* coords, const d
     CR_REQUIRE((coords || flexible) && tensors && offsets && tree && params, "null input");
     CR_REQUIRE(P >= 2 && tree_rows == 2 * P - 3, "tree must have 2P-3 rows");
     CR_REQUIRE(d >= 1 && padded_width(d) != 0, "tensor width > 192 is not supported by this build");
+    CR_REQUIRE(!flexible || d <= 32, "flexible progressive alignment: tensor width > 32 is not supported (no staged flexible provider)");
     CR_REQUIRE(offsets[0] == 0, "offsets[0] must be 0");
     for (int64_t s = 0; s < P; s++)
         CR_REQUIRE(offsets[s + 1] > offsets[s] && offsets[s + 1] - offsets[s] <= cr::kMaxLength,
@@ -465,8 +466,11 @@ static int progressive_align_impl(cr_context* ctx, const double* coords, const d
     const char* why = "CARETTA_SYNC_LEVELS is set";
     rc = g_cfg.sync_levels ? 1 : run_tree_planned(h, by_level, prm, gamma_weight, &why);
     if (rc < 0) return rc;
-    if (rc == 1 && flexible)                         // (CR_ERR_STATE = "not served by the device path": the host module then walks the tree itself)
-        return fail(CR_ERR_STATE, std::string("flexible progressive alignment is not served by the resident-tree path here: ") + why);
+    // CR_ERR_STATE = "valid input, not served by the device path": the host module then walks the tree itself.  run_level keeps
+    // the row features in registers (d <= 32) and has no flexible=True form.
+    if (rc == 1 && (flexible || d > 32))
+        return fail(CR_ERR_STATE, std::string(flexible ? "flexible progressive alignment" : "progressive alignment of tensors wider than 32") +
+                                      " is not served by the resident-tree path here: " + why);
     if (rc == 1) {                                  // not applicable, or a node outgrew the bound: level by level
         h->used = total;
         h->any_flags = 0;

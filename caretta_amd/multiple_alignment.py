@@ -93,18 +93,13 @@ class Protein(SequenceBase):
         xi, ti, xj, tj = f64(self.coordinates), f64(self.tensors), f64(other.coordinates), f64(other.tensors)
         if ti.shape[1] != tj.shape[1]:
             raise ValueError("tensor widths differ")
-        if ti.shape[1] > MAX_FUSED_TENSOR_WIDTH and (ti.shape[1] > MAX_STAGED_TENSOR_WIDTH or max(ti.shape[0], tj.shape[0]) > _STAGED_MAX_ROWS):
+        if _tensor_route(ti.shape[1], max(ti.shape[0], tj.shape[0])) == "host":
             return self._score_function_wide(xi, ti, xj, tj, other, gamma_tensor, gamma_coords, verbose)
         s = np.empty((xi.shape[0], xj.shape[0]))
         flags = C.c_uint32(0)
-        try:
-            check(_capi.load().cr_protein_score_function(default_context()._h, ptr(xi), ptr(ti), xi.shape[0], ptr(xj),
-                                                         ptr(tj), xj.shape[0], ti.shape[1], float(gamma_tensor),
-                                                         float(gamma_coords), ptr(s), C.byref(flags)))
-        except ValueError:
-            if ti.shape[1] <= MAX_FUSED_TENSOR_WIDTH:
-                raise
-            return self._score_function_wide(xi, ti, xj, tj, other, gamma_tensor, gamma_coords, verbose)   # (a pair the staged family cannot take)
+        check(_capi.load().cr_protein_score_function(default_context()._h, ptr(xi), ptr(ti), xi.shape[0], ptr(xj),
+                                                     ptr(tj), xj.shape[0], ti.shape[1], float(gamma_tensor),
+                                                     float(gamma_coords), ptr(s), C.byref(flags)))
         if flags.value & _capi.FLAG_SEED_ALL_ZERO:
             raise TypeError("tensor score matrix has no positive local alignment (reference: max_pos is None)")
         if (flags.value & _capi.FLAG_SEED_SKIPPED) and verbose:
@@ -243,14 +238,67 @@ class _NodeAttribute:
 
 
 # Tensor widths (csrc/cr_api.hip padded_width).  The reference takes any (L, d) array (multiple_alignment.py:312-319).
-#   d <= 32 : every kernel family (row features in registers, padded to 4 ... 32);
-#   d <= 192: the staged family only -- tensor scores by the run-time-width staging kernel, lists of at most 1 024 strips of 64 rows
-#             and structures of at most 2 048 residues: `pairwise` hands longer lists over in pieces;
-#   wider, or longer structures with d > 32: the same steps through the per-function drop-ins (the plugin route of
-#             make_pairwise_matrix / the host walk of progressive_align with Protein._score_function_wide).  Never an error.
+#   "fused"  d <= 32: every kernel family (row features in registers, padded to 4 ... 32);
+#   "staged" d <= 192, structures of at most 2 048 residues, not flexible=True: the staged family only -- tensor scores by the
+#            run-time-width staging kernel, lists of at most 1 024 strips of 64 rows: `pairwise` hands longer lists over in pieces;
+#   "host"   everything else: the same steps through the per-function drop-ins (the plugin route of make_pairwise_matrix /
+#            the host walk of progressive_align with Protein._score_function_wide).
+# _tensor_route is this rule; callers branch on its answer and check no width themselves.  Never an error for valid input.
 MAX_FUSED_TENSOR_WIDTH = 32
 MAX_STAGED_TENSOR_WIDTH = 192
 _STAGED_MAX_ROWS = 2048
+
+
+def _tensor_route(d: int, longest: int, flexible: bool = False) -> str:
+    """"fused", "staged" or "host": what serves tensors of width d on structures of at most `longest` residues."""
+    if d <= MAX_FUSED_TENSOR_WIDTH:
+        return "fused"
+    if d <= MAX_STAGED_TENSOR_WIDTH and longest <= _STAGED_MAX_ROWS and not flexible:
+        return "staged"
+    return "host"
+
+
+def _pairs_per_piece(offsets, pairs, d: int) -> int:
+    """Pairs of `pairs` (structure s = rows offsets[s] .. offsets[s + 1]) per run of one batch: all of them for d <= 32.
+    Wider tensors run on the staged family, which takes at most 1 024 strips of 64 rows and 2 GiB of staged scores per list
+    (cr_layout.h): a pair of n rows and m columns is strips x steps x rows-per-lane x 64 scores (cr_staged.h staged_shape),
+    the shape of a piece's longest pair."""
+    if d <= MAX_FUSED_TENSOR_WIDTH or not len(pairs):
+        return max(len(pairs), 1)
+    lengths = np.diff(offsets)
+    n, m_max = lengths[pairs[:, 0]], int(lengths[pairs[:, 1]].max())
+    rows_per_lane = np.maximum(1, -(-n // 512))
+    # (strips are not monotone in n -- 500 rows take 8 strips of one row per lane, 513 rows 5 of two --, so the bound is over
+    # every row count in the list: any of them may be the longest of a piece)
+    strips = -(-n // (64 * rows_per_lane))
+    steps = (m_max + 63 + 15) // 16 * 16 + 32
+    pair_scores = int((strips * rows_per_lane).max()) * 64 * steps
+    return max(1, min(1024 // int(strips.max()), (1 << 31) // (8 * pair_scores)))
+
+
+def _check_seed_flags(flags, pairs):
+    """The reference raises when a pair's tensor score matrix has no positive local alignment (its max_pos is None)."""
+    bad = np.flatnonzero(flags & _capi.FLAG_SEED_ALL_ZERO)
+    if len(bad):
+        raise TypeError(f"tensor score matrix of pair {tuple(pairs[bad[0]])} has no positive local alignment "
+                        "(reference: max_pos is None)")
+
+
+def _concatenate_pieces(pieces, scores_only):
+    """(sw, flags) or (results, alignments) of a pair list run in pieces, in pair order; alignment rows padded with -2 to
+    the widest piece."""
+    first = np.concatenate([p[0] for p in pieces])
+    if scores_only:
+        return first, np.concatenate([p[1] for p in pieces])
+    if pieces[0][1] is None:
+        return first, None
+    aln = np.full((len(first), 2, max(a.shape[2] for _, a in pieces)), -2, dtype=pieces[0][1].dtype)
+    at = 0
+    for _, a in pieces:
+        aln[at:at + len(a), :, :a.shape[2]] = a
+        at += len(a)
+    return first, aln
+
 
 _PLUGIN_BATCH_BYTES = 1 << 30      # score matrices of plugin sequences gathered on the host per batched launch
 
@@ -305,19 +353,15 @@ class MultipleAlignment:
     final_alignments = _NodeAttribute("final_alignments")
 
     # -- batched GPU path ---------------------------------------------------------------------
-    def _all_proteins(self, need_coordinates: bool = True) -> bool:
-        return all(type(s) is Protein and (s.coordinates is not None or not need_coordinates) for s in self.sequences)
-
-    def _fused_width(self, staged_ok: bool = True) -> bool:
-        """One tensor width for all sequences, and one the batched engine takes: up to 32 everywhere; up to 192 on staged scores
-        (structures of at most 2 048 residues; `staged_ok=False`: callers whose kernels keep the row features in registers)."""
+    def _route(self, flexible: bool = False) -> str:
+        """_tensor_route of these sequences; "host" for plugins, unequal tensor widths and, unless flexible, Proteins without
+        coordinates."""
+        if not all(type(s) is Protein and (flexible or s.coordinates is not None) for s in self.sequences):
+            return "host"
         widths = {np.shape(s.tensors)[1] for s in self.sequences}
         if len(widths) != 1:
-            return False
-        d = next(iter(widths))
-        if d <= MAX_FUSED_TENSOR_WIDTH:
-            return True
-        return staged_ok and d <= MAX_STAGED_TENSOR_WIDTH and max(len(s) for s in self.sequences) <= _STAGED_MAX_ROWS
+            return "host"
+        return _tensor_route(widths.pop(), max(len(s) for s in self.sequences), flexible)
 
     def pairwise(self, score_function_params=None, gap_open_penalty=1.0, gap_extend_penalty=0.01, pairs=None,
                  want_alignments=True, context: typing.Optional[Context] = None,
@@ -337,73 +381,32 @@ class MultipleAlignment:
             raise TypeError(f"unknown score_function parameters {sorted(prm)}")
         ctx = context or default_context()
         coords, tensors, offsets = pack_proteins(self.sequences, staging=True)
+        d = tensors.shape[1]
+        if flexible and _tensor_route(d, max(map(len, self.sequences)), flexible=True) == "host":
+            raise ValueError(f"flexible=True: tensors of width {d} have no batched path (the staged family has no flexible provider)")
         pairs = all_pairs(len(self.sequences)) if pairs is None else np.asarray(pairs, np.int32).reshape(-1, 2)
-        if tensors.shape[1] > MAX_FUSED_TENSOR_WIDTH and len(pairs):
-            return self._pairwise_in_pieces(ctx, coords, tensors, offsets, pairs, params, want_alignments, scores_only)
+        # (tensors wider than 32: the list in the pieces the staged family takes, on ONE batch -- structures uploaded once)
+        per_piece = _pairs_per_piece(offsets, pairs, d)
+        pieces = []
         batch = PairBatch(ctx, coords, tensors, offsets)
         try:
-            batch.set_pairs(pairs)
-            batch.run(params, scores_only=scores_only, flexible=flexible)
-            if scores_only:                       # the matrix entries only: 12 bytes per pair come back
-                sw, flags = batch.fetch_scores()
-                # (two columns, not a zeroed PAIR_RESULT record per pair: 21 MB of host memory at 512 structures that nobody
-                # reads, 5 ms to fault in, and allocator churn of that size is what used to delay the next kernel --
-                # DESIGN.md section 8)
-                res, aln = np.zeros(len(pairs), dtype=[("sw", np.float64), ("flags", np.uint32)]), None
-                res["sw"], res["flags"] = sw, flags
-            else:
-                res, aln = batch.fetch(want_alignments)
-        finally:
-            batch.close()
-        if np.any(res["flags"] & _capi.FLAG_SEED_ALL_ZERO):
-            bad = pairs[np.nonzero(res["flags"] & _capi.FLAG_SEED_ALL_ZERO)[0][0]]
-            raise TypeError(f"tensor score matrix of pair {tuple(bad)} has no positive local alignment "
-                            "(reference: max_pos is None)")
-        return PairwiseResults(pairs, res, aln)
-
-    def _pairwise_in_pieces(self, ctx, coords, tensors, offsets, pairs, params, want_alignments, scores_only):
-        """`pairwise` for tensors wider than 32: the staged family takes at most 1 024 strips of 64 rows (and 2 GiB of staged
-        scores) per pair list, so the list goes over in pieces on ONE batch (structures uploaded once); results in pair order."""
-        lengths = np.diff(offsets)
-        n_max = int(lengths[pairs[:, 0]].max())
-        m_max = int(lengths[pairs[:, 1]].max())
-        rows_per_lane = max(1, -(-n_max // 512))
-        strips = -(-n_max // (64 * rows_per_lane))
-        steps = (m_max + 63 + 15) // 16 * 16 + 32
-        per_piece = max(1, min(1024 // strips, int((1 << 31) // (8 * strips * steps * rows_per_lane * 64))))
-        sw_parts, flag_parts, res_parts, aln_parts = [], [], [], []
-        batch = PairBatch(ctx, coords, tensors, offsets)
-        try:
-            for lo in range(0, len(pairs), per_piece):
+            for lo in range(0, max(len(pairs), 1), per_piece):
                 batch.set_pairs(pairs[lo:lo + per_piece])
-                batch.run(params, scores_only=scores_only)
-                if scores_only:
-                    sw, flags = batch.fetch_scores()
-                    sw_parts.append(sw.copy())
-                    flag_parts.append(flags.copy())
-                else:
-                    r, a = batch.fetch(want_alignments)
-                    res_parts.append(r.copy())
-                    aln_parts.append(None if a is None else a.copy())
+                batch.run(params, scores_only=scores_only, flexible=flexible)
+                # (scores only: the matrix entries, 12 bytes per pair come back)
+                pieces.append(batch.fetch_scores() if scores_only else batch.fetch(want_alignments))
         finally:
             batch.close()
+        first, second = pieces[0] if len(pieces) == 1 else _concatenate_pieces(pieces, scores_only)
         if scores_only:
+            # (two columns, not a zeroed PAIR_RESULT record per pair: 21 MB of host memory at 512 structures that nobody
+            # reads, 5 ms to fault in, and allocator churn of that size is what used to delay the next kernel --
+            # DESIGN.md section 8)
             res, aln = np.zeros(len(pairs), dtype=[("sw", np.float64), ("flags", np.uint32)]), None
-            res["sw"], res["flags"] = np.concatenate(sw_parts), np.concatenate(flag_parts)
+            res["sw"], res["flags"] = first, second
         else:
-            res = np.concatenate(res_parts)
-            aln = None
-            if want_alignments:
-                stride = max(a.shape[2] for a in aln_parts)
-                aln = np.full((len(pairs), 2, stride), -2, dtype=aln_parts[0].dtype)
-                at = 0
-                for a in aln_parts:
-                    aln[at:at + len(a), :, :a.shape[2]] = a
-                    at += len(a)
-        if np.any(res["flags"] & _capi.FLAG_SEED_ALL_ZERO):
-            bad = pairs[np.nonzero(res["flags"] & _capi.FLAG_SEED_ALL_ZERO)[0][0]]
-            raise TypeError(f"tensor score matrix of pair {tuple(bad)} has no positive local alignment "
-                            "(reference: max_pos is None)")
+            res, aln = first, second
+        _check_seed_flags(res["flags"], pairs)
         return PairwiseResults(pairs, res, aln)
 
     def _pairwise_matrix_multi(self, multi, score_function_params=None):
@@ -419,10 +422,7 @@ class MultipleAlignment:
         coords, tensors, offsets = pack_proteins(self.sequences)
         sw, flags = multi.pairwise_scores(coords, tensors, offsets, params)
         pairs = all_pairs(num)
-        if np.any(flags & _capi.FLAG_SEED_ALL_ZERO):
-            bad = pairs[np.nonzero(flags & _capi.FLAG_SEED_ALL_ZERO)[0][0]]
-            raise TypeError(f"tensor score matrix of pair {tuple(bad)} has no positive local alignment "
-                            "(reference: max_pos is None)")
+        _check_seed_flags(flags, pairs)
         return assemble_matrix(pairs, sw, num)
 
     def make_pairwise_matrix(self, score_function_params=None):
@@ -432,10 +432,11 @@ class MultipleAlignment:
         num = len(self.sequences)
         if num < 2:
             return np.zeros((num, num))
-        if self._all_proteins() and self._fused_width() and not score_function_params.get("flexible", False):
+        flexible = bool(score_function_params.get("flexible", False))
+        route = self._route(flexible)
+        if route == "fused" and not flexible:
             from . import engine
-            npairs = num * (num - 1) // 2
-            if npairs >= engine.MULTI_DEVICE_MIN_PAIRS and self._fused_width(staged_ok=False):
+            if num * (num - 1) // 2 >= engine.MULTI_DEVICE_MIN_PAIRS:
                 # several GPUs visible to (and owned by) this process: the pair set dealt over all of them, one RCCL
                 # all-gather.  A fault of the multi-device machinery (communicator set-up, a device that cannot be opened)
                 # is not a fault of the input: say so ONCE, remember it, and compute the same matrix on one device.
@@ -447,18 +448,9 @@ class MultipleAlignment:
                     import warnings
                     engine.multi_device_failed()
                     warnings.warn(f"multi-GPU pairwise matrix failed ({exc}); running on one device from now on", RuntimeWarning)
-            try:
-                out = self.pairwise(score_function_params, want_alignments=False, scores_only=True)
-                return assemble_matrix(out.pairs, out.results["sw"], num)
-            except ValueError:
-                # (tensors wider than 32 run on staged scores only: a list even one pair of which does not fit them -- alignment
-                # columns beyond the LDS -- takes the plugin route below)
-                if np.shape(self.sequences[0].tensors)[1] <= MAX_FUSED_TENSOR_WIDTH:
-                    raise
-        if (score_function_params.get("flexible", False) and self._all_proteins(need_coordinates=False)
-                and self._fused_width(staged_ok=False)):      # (wider tensors: the plugin route below)
-            # flexible=True: smith_waterman_score of the tensor score matrix of every pair (multiple_alignment.py:323-326,
-            # :164), one launch over the pair list (cr_batch_run_tensor_scores)
+        if route != "host":
+            # one batched launch sequence over the pair list; flexible=True: smith_waterman_score of the tensor score matrix
+            # of every pair (multiple_alignment.py:323-326, :164), one launch (cr_batch_run_tensor_scores)
             out = self.pairwise(score_function_params, want_alignments=False, scores_only=True)
             return assemble_matrix(out.pairs, out.results["sw"], num)
         # third-party SequenceBase plugins: the score matrices come from the plugin's own score_function (its Python),
@@ -494,40 +486,30 @@ class MultipleAlignment:
         score_function_params = score_function_params or {}
         tree = np.asarray(tree)
         flex_score, flex_mean = bool(score_function_params.get("flexible", False)), bool(mean_function_params.get("flexible", False))
-        if (len(self.sequences) >= 2 and tree.shape == (2 * len(self.sequences) - 3, 2)
-                and all(type(s) is Protein and s.coordinates is not None for s in self.sequences)
-                and self._fused_width() and not flex_score and not flex_mean):
-            # every node of the tree on the device, one launch pair per tree level (cr_progressive_align)
-            wide = np.shape(self.sequences[0].tensors)[1] > MAX_FUSED_TENSOR_WIDTH
+        if (len(self.sequences) >= 2 and tree.shape == (2 * len(self.sequences) - 3, 2) and flex_score == flex_mean
+                and self._route(flex_score) != "host"):
+            # every node of the tree on the device, one launch pair per tree level (cr_progressive_align); flexible=True in score
+            # AND mean function (multiple_alignment.py:323-326, :351-362): nodes are tensors and consensus weights only -- the same
+            # resident tree without the seed stage (cr_progressive_align_flexible).  CR_ERR_STATE: the input is valid but a node
+            # outgrew what the device path serves for this width -- the host walk below.  Every other error is raised.
             try:
                 return self._progressive_align_resident(tree, gap_open_penalty, gap_extend_penalty, consensus_weight,
-                                                        gamma_weight, score_function_params, mean_function_params)
-            except (_capi.CarettaHipError, ValueError):
-                if not wide:
-                    raise
-                # (tensors wider than 32 run on staged scores only: a tree whose nodes outgrow them takes the host walk below)
-        if (len(self.sequences) >= 2 and tree.shape == (2 * len(self.sequences) - 3, 2) and flex_score and flex_mean
-                and self._all_proteins(need_coordinates=False) and self._fused_width(staged_ok=False)):
-            # flexible=True in score AND mean function (multiple_alignment.py:323-326, :351-362): nodes are tensors and consensus
-            # weights only -- the same resident tree without the seed stage (cr_progressive_align_flexible).  A node that outgrows
-            # the launch bound sends the tree to the host walk below.
-            try:
-                return self._progressive_align_resident(tree, gap_open_penalty, gap_extend_penalty, consensus_weight,
-                                                        gamma_weight, score_function_params, mean_function_params, flexible=True)
+                                                        gamma_weight, score_function_params, mean_function_params, flexible=flex_score)
             except _capi.CarettaHipError as exc:
                 if exc.code != _capi.CR_ERR_STATE:
                     raise
         self._drop_pending_nodes()
         walk = _GuideTreeWalk(self.sequences, consensus_weight)
-        fusable = not score_function_params.get("flexible", False) and not mean_function_params.get("flexible", False)
+        fusable = not flex_score and not flex_mean
 
         def align_children(s1, s2, w1, w2, name_int):
             """One tree node: (aln_1, aln_2, the new consensus sequence, its consensus weights)."""
             size_1, size_2 = len(walk.members[s1.name]), len(walk.members[s2.name])
             mult_1, mult_2 = size_2 / (2 * (size_1 + size_2)), size_1 / (2 * (size_1 + size_2))       # :199-202
             if (fusable and type(s1) is Protein and type(s2) is Protein and s1.coordinates is not None
-                    and s2.coordinates is not None and np.shape(s1.tensors)[1] <= MAX_FUSED_TENSOR_WIDTH):      # (cr_progressive_node: registers)
+                    and s2.coordinates is not None and _tensor_route(np.shape(s1.tensors)[1], max(len(s1), len(s2))) == "fused"):
                 # the whole node (score matrices, dtw_align, mean_function, get_mean_weights) in two launches
+                # (cr_progressive_node keeps the row features in registers)
                 return _progressive_node(s1, s2, w1, w2, mult_1, mult_2, name_int, gap_open_penalty, gap_extend_penalty,
                                          gamma_weight, score_function_params, mean_function_params)
             # third-party SequenceBase plugins: their score / mean functions around the HIP dtw_align (:204-217)
@@ -673,8 +655,7 @@ class MultipleAlignment:
         """multiple_alignment.py:255-285"""
         mean_function_params = mean_function_params or {}
         score_function_params = score_function_params or {}
-        if (len(self.sequences) == 2 and self._all_proteins() and self._fused_width()
-                and not score_function_params.get("flexible", False)):
+        if len(self.sequences) == 2 and not score_function_params.get("flexible", False) and self._route() != "host":
             # :263-275 is pipeline H of this one pair: both score matrices, the seed and dtw_align in two launches
             out = self.pairwise(score_function_params, gap_open_penalty, gap_extend_penalty)
             if score_function_params.get("verbose", True) and out.results["flags"][0] & _capi.FLAG_SEED_SKIPPED:

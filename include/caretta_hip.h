@@ -127,7 +127,9 @@ int cr_batch_run_scores(cr_batch *b, const cr_params *params, double *d_sw_out);
 /* flexible=True: Protein.score_function short-circuits to the tensor score matrix (multiple_alignment.py:323-326), whose
  * smith_waterman_score (gap 0, dynamic_time_warping.py:205-222) is the P x P matrix entry (:164).  One launch over the pair
  * list; only gamma_tensor of `params` is read; afterwards cr_batch_fetch_scores has the entries (flags are 0: this path of
- * the reference raises nothing).  d_sw_out as for cr_batch_run. */
+ * the reference raises nothing).  d_sw_out as for cr_batch_run.  Tensor widths up to 32 only: a batch with d > 32 is
+ * CR_ERR_ARGUMENT on entry, before any launch (the staged family has no flexible provider; the caller routes such tensors to
+ * the host before it calls). */
 int cr_batch_run_tensor_scores(cr_batch *b, const cr_params *params, double *d_sw_out);
 /* Synchronise and copy results to host.  Any pointer may be NULL.  results[npairs];
  * aln i64[npairs, 2, aln_stride] (rows padded with -2 after aln_len; aln_stride >= max(n+m)). */
@@ -229,7 +231,11 @@ int cr_progressive_node(cr_context *ctx, const double *coords_1, const double *t
  * tree: uint64 (tree_rows = 2P-3, 2) exactly as neighbor_joining returns it (neighbor_joining.py:19-95): rows
  * 2x, 2x+1 = (child, P + x) for x = 0 .. P-3, last row = the two nodes joined by the final node (:244-247).
  * Leaf weights are `consensus_weight` everywhere (:189-193).  Internal nodes are numbered 0 .. P-2 in creation
- * order (node id P + k; the final node is k = P-2). */
+ * order (node id P + k; the final node is k = P-2).
+ * Errors: CR_ERR_ARGUMENT (-> ValueError) is bad input or a width the entry is never built for (d > 192; flexible with
+ * d > 32): the caller routes before it calls.  CR_ERR_STATE means the input is valid but the device path does not serve this
+ * tree at this width -- with d > 32 (staged scores only) when the resident tree does not apply or a node outgrows its launch
+ * bound (1.5 x the longest structure, at most 2048 columns): the only error after which the caller walks the tree itself. */
 typedef struct cr_progressive cr_progressive;
 int cr_progressive_align(cr_context *ctx, const double *coords, const double *tensors, const int64_t *offsets,
                          int64_t num_structures, int64_t d, const uint64_t *tree, int64_t tree_rows,
@@ -237,8 +243,9 @@ int cr_progressive_align(cr_context *ctx, const double *coords, const double *te
                          cr_progressive **out);
 /* The same with flexible=True in the score function AND the mean function (multiple_alignment.py:323-326: the score matrix of
  * two nodes is the tensor RBF alone; :351-362: a node is its mean tensors, no coordinates): tensors f64[total][d] only.
- * cr_progressive_fetch_nodes then takes coords == NULL.  CR_ERR_STATE when a node outgrows the launch bound (1.5 x the
- * longest structure, at most 2048 columns): the caller walks the tree itself (cr_dtw_align per node). */
+ * cr_progressive_fetch_nodes then takes coords == NULL.  Tensor widths up to 32 only: d > 32 is CR_ERR_ARGUMENT before
+ * anything is allocated or uploaded.  CR_ERR_STATE when the resident tree does not apply or a node outgrows the launch bound
+ * (1.5 x the longest structure, at most 2048 columns): the caller walks the tree itself (cr_dtw_align per node). */
 int cr_progressive_align_flexible(cr_context *ctx, const double *tensors, const int64_t *offsets, int64_t num_structures, int64_t d,
                                   const uint64_t *tree, int64_t tree_rows, const cr_params *params, double consensus_weight,
                                   double gamma_weight, cr_progressive **out);

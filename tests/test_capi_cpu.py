@@ -319,3 +319,56 @@ def test_size_classes_on_the_host(lib, monkeypatch):
     # a pair index out of range is an argument error, as in cr_batch_set_pairs
     with pytest.raises(ValueError):
         engine.plan_layout(offsets, 10, np.array([[0, 160]], np.int32))
+
+
+
+def test_tensor_route_boundaries(lib):
+    """multiple_alignment._tensor_route, the one rule that sends tensors to the fused kernels, the staged family or the host
+    drop-ins, at each of its boundaries; MultipleAlignment._route asks it for a family of one width (with coordinates unless
+    flexible=True) and answers "host" for anything else."""
+    from caretta_amd import multiple_alignment as ma
+    route = ma._tensor_route
+    assert route(32, 4000) == "fused" and route(33, 100) == "staged"
+    assert route(192, 2048) == "staged" and route(193, 100) == "host"
+    assert route(33, 2048) == "staged" and route(33, 2049) == "host" and route(192, 2049) == "host"
+    assert route(32, 100, flexible=True) == "fused" and route(33, 100, flexible=True) == "host"
+
+    class Plugin(ma.Protein):
+        pass
+
+    x, t = np.zeros((5, 3)), np.zeros((5, 48))
+    assert ma.MultipleAlignment([ma.Protein("a", t, x), ma.Protein("b", t, x)])._route() == "staged"
+    assert ma.MultipleAlignment([ma.Protein("a", t), ma.Protein("b", t, x)])._route() == "host"
+    assert ma.MultipleAlignment([ma.Protein("a", t[:, :16]), ma.Protein("b", t[:, :16])])._route(flexible=True) == "fused"
+    assert ma.MultipleAlignment([ma.Protein("a", t, x), ma.Protein("b", t[:, :40], x)])._route() == "host"
+    assert ma.MultipleAlignment([ma.Protein("a", t, x), Plugin("b", t, x)])._route() == "host"
+
+
+@pytest.mark.parametrize("dim", [33, 64, 192])
+def test_wide_tensor_pieces_are_staged_lists_on_the_host(lib, dim):
+    """Tensors wider than 32 run on the staged family only, which takes a bounded list (1 024 strips of 64 rows, 2 GiB of staged
+    scores): `MultipleAlignment.pairwise` hands longer lists over in pieces of multiple_alignment._pairs_per_piece pairs.  Every
+    piece of a list that needs one, two or many of them is ONE staged list for cr_plan_layout, equal or ragged lengths; one pair
+    more than a piece of equal lengths is refused (a piece is as large as the library allows)."""
+    from caretta_amd import engine
+    from caretta_amd import multiple_alignment as ma
+    rng = np.random.default_rng(dim)
+    for longest in (64, 300, 511, 512, 513, 1024, 1025, 2048):
+        full = ma._pairs_per_piece(*_equal_family(longest, 1), dim)
+        for npairs, pieces in ((full, 1), (full + 1, 2), (3 * full + 5, 4)):
+            offsets, pairs = _equal_family(longest, npairs)
+            for ragged in (False, True):
+                if ragged:                  # the same pairs, every structure but the first shorter
+                    lengths = np.diff(offsets)
+                    lengths[1:] = rng.integers(longest // 2, longest + 1, size=len(lengths) - 1)
+                    offsets = np.concatenate([[0], np.cumsum(lengths)])
+                step = ma._pairs_per_piece(offsets, pairs, dim)
+                if not ragged:
+                    assert step == full and -(-npairs // step) == pieces
+                for lo in range(0, npairs, step):
+                    piece = pairs[lo:lo + step]
+                    parts, _ = engine.plan_layout(offsets, dim, piece)
+                    assert len(parts) == 1 and parts[0][0] == "staged" and parts[0][4] == len(piece), (longest, npairs, ragged, parts)
+        offsets, pairs = _equal_family(longest, full + 1)
+        with pytest.raises(ValueError):
+            engine.plan_layout(offsets, dim, pairs)

@@ -555,7 +555,6 @@ def test_wide_tensor_lists_in_pieces_vs_oracle(ctx, oracle, dim, num, length, ga
     C ABI itself refuses the list that is too long for one piece with an argument error."""
     from caretta_amd import engine
     from caretta_amd import multiple_alignment as ma
-    from caretta_amd._capi import CarettaHipError
     from oracle.pyoracle import default_params
     fam = synthetic.make_family(num, length, dim=dim, seed=7300 + dim, ragged=(num % 2 == 1), clades=3)
     coords, tensors, offsets = synthetic.pack(fam)
@@ -580,6 +579,42 @@ def test_wide_tensor_lists_in_pieces_vs_oracle(ctx, oracle, dim, num, length, ga
     for key in ("sw", "dtw_score", "seed_score", "rmsd", "coverage", "tm"):
         assert np.array_equal(res[key], ref[key][:len(piece)]), key
     if len(pairs) * (-(-length // 64)) > 1024:
-        with pytest.raises((CarettaHipError, ValueError)):
+        with pytest.raises(ValueError):
             batch.set_pairs(pairs)
     batch.close()
+
+
+def test_wide_tensors_are_routed_up_front_and_errors_surface(ctx):
+    """Tensors wider than 32 are routed before any call (multiple_alignment._tensor_route), so an error is an error.
+    flexible=True with d = 48 has no batched path: `pairwise` raises ValueError before a batch exists, and the library refuses
+    it too before any work (cr_batch_run_tensor_scores, cr_progressive_align_flexible: CR_ERR_ARGUMENT).  A NaN in the
+    tensors of a staged family is the batched path's ValueError from make_pairwise_matrix and progressive_align, not a detour
+    through the host route."""
+    import ctypes as C
+    from caretta_amd import _capi, engine
+    from caretta_amd import multiple_alignment as ma
+    fam = synthetic.make_family(5, 60, dim=48, seed=7400)
+    prots = [ma.Protein(s.name, s.tensors, s.coordinates, s.sequence) for s in fam]
+    with pytest.raises(ValueError, match="flexible=True"):
+        ma.MultipleAlignment(prots).pairwise(dict(flexible=True, gamma_tensor=1.5), scores_only=True, want_alignments=False)
+    coords, tensors, offsets = synthetic.pack(fam)
+    tensors, offsets = _capi.f64(tensors), _capi.i64(offsets)
+    batch = engine.PairBatch(ctx, coords, tensors, offsets).set_pairs(engine.all_pairs(len(fam)))
+    with pytest.raises(ValueError, match="tensor width > 32"):
+        batch.run(engine.make_params(gamma_tensor=1.5), scores_only=True, flexible=True)
+    batch.close()
+    # rows 2x, 2x + 1 = (child, P + x); the last row joins the final node's children
+    tree = np.array([[0, 5], [1, 5], [2, 6], [3, 6], [4, 7], [5, 7], [6, 7]], dtype=np.uint64)
+    lib, prm, h = _capi.load(), engine.make_params(gamma_tensor=1.5), C.c_void_p()
+    rc = lib.cr_progressive_align_flexible(ctx._h, _capi.ptr(tensors), _capi.ptr(offsets), len(fam), 48, _capi.ptr(tree),
+                                           tree.shape[0], C.byref(prm), 1.0, 1.0, C.byref(h))
+    assert rc == _capi.CR_ERR_ARGUMENT and not h.value
+    assert "tensor width > 32" in lib.cr_last_error().decode()
+    nan = [ma.Protein(p.name, np.array(p.tensors), p.coordinates, p.sequence) for p in prots]
+    nan[2].tensors[7, 11] = np.nan
+    msa = ma.MultipleAlignment(nan)
+    sf = dict(gamma_tensor=1.5, gamma_coords=0.03, verbose=False)
+    with pytest.raises(ValueError, match="tensors contain NaN or infinity"):
+        msa.make_pairwise_matrix(sf)
+    with pytest.raises(ValueError, match="tensors contain NaN or infinity"):
+        msa.progressive_align(tree, 1.0, 0.01, 1.0, 1.0, sf, dict(verbose=False))
